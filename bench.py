@@ -5,6 +5,9 @@ for N > 1 either launch under `python -m torch.distributed.run --nproc-per-node 
 or run `bench.py --gpus N` directly: without a launcher it starts the N ranks itself
 (pytorchdistributed_amd/bench/common.py:launch_ranks).
 Rank 0 prints one JSON line.  See pytorchdistributed_amd/bench/resnet_ddp.py.
+`--dump-outputs DIR` also writes the last timed step's loss, logits and a sample of the updated parameters
+as DIR/<name>.npy, from a run on the fixed-order sums (repeatable, slower than the headline); `--full` is
+where secondary measurements go (the headline run has none).
 """
 import os
 import sys

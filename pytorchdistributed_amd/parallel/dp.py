@@ -97,6 +97,26 @@ class _CopyInto(torch.autograd.Function):
         return g.to(ctx.src_device, non_blocking=True), None
 
 
+def _skeleton(module: tnn.Module) -> tnn.Module:
+    """A shallow copy of the module tree with its own ``_parameters`` / ``_buffers`` / ``_modules`` dicts
+    (the tensors are shared).  ``functional_call`` swaps tensors into those dicts for the duration of the
+    call, so the per-device threads must not share them: two threads on one module restore each other's
+    replica views as the module's parameters.  Only registered submodules (``_modules``) are copied: one a
+    module reaches through a plain attribute or a Python list still is the shared original.  Rebuilt on
+    every forward (one shallow copy per module, like torch's replicate), so it never goes stale."""
+    copies = {}
+    for m in module.modules():
+        c = m.__new__(type(m))
+        c.__dict__ = m.__dict__.copy()
+        c._parameters, c._buffers, c._modules = dict(m._parameters), dict(m._buffers), dict(m._modules)
+        copies[m] = c
+    for c in copies.values():
+        for k, child in c._modules.items():
+            if child is not None:
+                c._modules[k] = copies[child]
+    return copies[module]
+
+
 class DataParallel(tnn.Module):
     def __init__(self, module: tnn.Module, device_ids: Optional[Sequence] = None, output_device=None, dim: int = 0):
         super().__init__()
@@ -207,6 +227,9 @@ class DataParallel(tnn.Module):
         results: List = [None] * n
         errors: List = [None] * n
         grad_enabled = torch.is_grad_enabled()
+        # the master runs on the module itself (its state is the module's own tensors), every other
+        # device's thread on a skeleton of its own
+        mods = [self.module] + [_skeleton(self.module) for _ in range(1, n)]
 
         def work(i):
             try:
@@ -214,9 +237,9 @@ class DataParallel(tnn.Module):
                 dev = devs[i]
                 if dev.type == "cuda":
                     with torch.cuda.device(dev), torch.cuda.stream(torch.cuda.current_stream(dev)):
-                        results[i] = functional_call(self.module, states[i], tuple(scattered[i]), kwargs)
+                        results[i] = functional_call(mods[i], states[i], tuple(scattered[i]), kwargs)
                 else:
-                    results[i] = functional_call(self.module, states[i], tuple(scattered[i]), kwargs)
+                    results[i] = functional_call(mods[i], states[i], tuple(scattered[i]), kwargs)
             except BaseException as e:  # noqa: BLE001
                 errors[i] = e
 

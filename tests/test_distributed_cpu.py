@@ -224,6 +224,37 @@ def test_bench_launches_its_own_ranks():
     assert rec["backend"] == "gloo" and rec["config"]["global_batch"] == 2 * rec["config"]["per_gpu_batch"]
 
 
+def test_bench_dump_outputs_repeatable(tmp_path, monkeypatch):
+    """`--dump-outputs DIR` writes the last timed step's loss, logits and parameter sample as float32
+    .npy files; the seeded run repeats them exactly; `--steps` is the number of timed steps and the line
+    carries `ms_per_step`; `--full` is accepted.  A second value of `--steps` runs that many."""
+    import json
+
+    import numpy as np
+
+    monkeypatch.delenv("PDA_DETERMINISTIC", raising=False)
+    got = []
+    for d, extra in ((tmp_path / "a", []), (tmp_path / "b", ["--full"])):
+        r = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(d)] + extra)
+        assert r.returncode == 0, r.stderr[-3000:]
+        rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        # the step count is counted by the run (losses recorded after the warm-up), not echoed
+        assert rec["steps"] == 2 and rec["timed_steps_run"] == 2 and rec["ms_per_step"] > 0
+        assert rec["fixed_order_sums"] is True  # a dumping run asks for the fixed-order sums
+        assert sorted(p.name for p in d.iterdir()) == ["logits.npy", "loss.npy", "params_sample.npy"]
+        arrs = {p.stem: np.load(p) for p in d.iterdir()}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert arrs["logits"].shape == (rec["config"]["per_gpu_batch"], 1000) and arrs["loss"].shape == (1,)
+        assert abs(float(arrs["loss"][0]) - rec["final_loss"]) < 1e-3
+        got.append(arrs)
+    for k in got[0]:
+        assert np.array_equal(got[0][k], got[1][k]), k
+    r = _bench(["--gpus", "1", "--steps", "3", "--warmup", "0"])
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert rec["timed_steps_run"] == 3 and rec["fixed_order_sums"] is False
+
+
 def test_bench_refuses_mismatched_world():
     """Under a launcher whose WORLD_SIZE disagrees with --gpus the bench refuses (never downgrades)."""
     r = _bench(["--gpus", "2", "--steps", "1", "--warmup", "0"], env={"WORLD_SIZE": "1", "RANK": "0",

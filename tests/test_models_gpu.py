@@ -532,3 +532,33 @@ def test_deterministic_mode_bit_identical(monkeypatch):
     assert torch.equal(l1, l2), (l1, l2)
     assert all(torch.equal(a, b) for a, b in zip(p1, p2))
     assert all(torch.equal(a, b) for a, b in zip(b1, b2))
+
+
+def test_bench_dump_outputs_bit_identical_runs(tmp_path):
+    """`bench.py --dump-outputs` end to end: two runs with the same arguments write bit-identical loss,
+    logits and parameter samples.  Batch 16 at 224 x 224 gives the stem and layer1 BNs 200 704 and 50 176
+    rows, more than the 256 * 64 below which the default kernels already sum in a fixed order, so the run
+    repeats only because it switches to the fixed-order sums; the line says so and counts its steps."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k != "PDA_DETERMINISTIC"}
+    got = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2",
+                            "--warmup", "1", "--batch", "16", "--dump-outputs", str(d)], cwd=root, env=env,
+                           capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-3000:]
+        rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert rec["fixed_order_sums"] is True and rec["timed_steps_run"] == 2 and rec["dtype"] == "bf16"
+        got.append({f.stem: np.load(f) for f in d.iterdir()})
+        assert sorted(got[-1]) == ["logits", "loss", "params_sample"]
+        assert got[-1]["logits"].shape == (16, 1000) and np.isfinite(got[-1]["logits"]).all()
+    for k in got[0]:
+        assert np.array_equal(got[0][k], got[1][k]), k

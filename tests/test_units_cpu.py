@@ -1,5 +1,6 @@
 """Single-process CPU unit tests: sampler parity, bucket reducer, native store,
 optimizers' reference math, model shapes / parameter counts, log format, checkpoint layout."""
+import sys
 import threading
 
 import pytest
@@ -428,3 +429,30 @@ def test_data_parallel_coalesced_replicas_match_single_device():
     net[3].weight = tnn.Parameter(torch.zeros(3, 8))
     st4 = dp._replica_states([torch.device("cpu"), torch.device("cpu")])
     assert torch.equal(st4[1]["3.weight"], torch.zeros(3, 8))
+
+
+def test_data_parallel_threads_leave_the_module_intact():
+    """The per-device threads of a DataParallel forward must not swap tensors through one shared module:
+    with the interpreter switching threads as often as it can, after every forward + backward the
+    wrapped module's parameters are still its own leaf tensors and all have gradients."""
+    import torch.nn as tnn
+
+    from pytorchdistributed_amd.parallel.dp import DataParallel
+
+    torch.manual_seed(0)
+    net = tnn.Sequential(tnn.Linear(6, 8), tnn.BatchNorm1d(8), tnn.ReLU(), tnn.Linear(8, 3))
+    dp = DataParallel(net, device_ids=["cpu", "cpu", "cpu"])
+    dp._force_copy = True
+    own = [p for p in net.parameters()]
+    x = torch.randn(12, 6)
+    interval = sys.getswitchinterval()
+    sys.setswitchinterval(1e-6)
+    try:
+        for it in range(100):
+            net.zero_grad()
+            dp(x).square().sum().backward()
+            now = list(net.parameters())
+            assert all(a is b for a, b in zip(own, now)), it
+            assert all(p.is_leaf and p.grad is not None for p in now), it
+    finally:
+        sys.setswitchinterval(interval)
